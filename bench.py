@@ -12,10 +12,13 @@ rank processes itself -- from a parent that never touches the GPU -- and exits w
 no data-path collective ("weak" scaling); timing is barrier + synchronize on both sides, max over ranks; rank 0 prints the line,
 with the world size RCCL reported and every rank's own time so a straggler is visible.
 
-Prints ONE JSON line with the contract fields plus
+A plain run sets up, warms up, times the K steps and prints ONE JSON line with the contract fields (metric, value, unit,
+higher_is_better, dtype, ms_per_step, ...).  `--full` adds what takes runs of its own:
   roofline      dominant kernel (fused conv3x3(d2)+IndRNN layer, fp32 MFMA): algorithmic FLOPs / HIP-event time
   roofline_fft  the FFT+DC step (log_likelihood_gradient) against the HBM roofline, (25+16C)*H*W bytes per slice-step
   cpu_baseline  the CPU oracle (restatement of the reference's torch-CPU path) on a bounded sample, rank 0, N=1 only
+  and the concurrent-replay check, the streamed-input figure and the other configurations (`other_configs`, `exact_fp32_route`).
+`--dump-outputs DIR` writes what the timed path returned in its last step as DIR/<name>.npy (float32 / float64, <= 64 MB in all).
 """
 import argparse
 import json
@@ -88,6 +91,12 @@ def parse():
     ap.add_argument("--cpu-slices", type=int, default=3,
                     help="timed slices of the CPU-baseline leg after its warm-up (BASELINE.md section 3: >= 3; mean and min are reported)")
     ap.add_argument("--dist-selftest", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: HIP-event kernel breakdown and rooflines, the concurrent-replay check, the CPU baseline "
+                         "and parity against the oracle, the streamed-input figure and the other configurations (each still switched off by its --no-* flag)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float32 / float64, at most "
+                         "64 MB in all: larger outputs as a fixed, seeded sample); rank 0 only")
     args = ap.parse_args()
     args.stream_inputs = not args.no_stream_inputs
     if args.streams <= 0:
@@ -319,6 +328,73 @@ def _tensors(o):
     return []
 
 
+DUMP_LIMIT_BYTES = 64_000_000     # --dump-outputs: all files together, npy headers included
+DUMP_SAMPLE_SEED = 0
+
+
+def _named_leaves(o, name="out"):
+    """(name, tensor) for every tensor of a nested output, named by its index path: CIRIM's list[cascade][time_step] -> out_<cascade>_<step>."""
+    if isinstance(o, torch.Tensor):
+        return [(name, o)]
+    if isinstance(o, (list, tuple)):
+        return [nt for i, e in enumerate(o) for nt in _named_leaves(e, f"{name}_{i}")]
+    if isinstance(o, dict):
+        return [nt for k, e in o.items() for nt in _named_leaves(e, f"{name}_{k}")]
+    return []
+
+
+def _dump_itemsize(t):
+    return {torch.complex128: 16, torch.complex64: 8, torch.float64: 8}.get(t.dtype, 4)
+
+
+def write_outputs(path, outs):
+    """--dump-outputs: what the timed path returned in its last step.  `outs` = one nested output per stream (the same structure each); every
+    leaf is written as path/<name>.npy with the streams stacked on a new leading axis, complex as a trailing (re, im) axis, in float64 if it is
+    double precision and float32 otherwise.  If the whole set exceeds DUMP_LIMIT_BYTES, the LAST leaf (the final result) is written whole and
+    every other leaf as the same number of elements at flat indices drawn once from a fixed seed, so that two runs with the same arguments
+    write files that compare element for element."""
+    import numpy as np
+    leaves = [_named_leaves(o) for o in outs]
+    names = [n for n, _ in leaves[0]]
+    stacked = {n: [lv[j][1] for lv in leaves] for j, n in enumerate(names)}
+    header = 256                                      # bytes per .npy header, generously
+    numel = {n: sum(t.numel() for t in ts) for n, ts in stacked.items()}
+    nbytes = {n: numel[n] * _dump_itemsize(ts[0]) for n, ts in stacked.items()}
+    sample = None
+    if sum(nbytes.values()) + header * len(names) > DUMP_LIMIT_BYTES:
+        last, rest = names[-1], names[:-1]
+        whole = nbytes[last] if nbytes[last] <= DUMP_LIMIT_BYTES // 2 else 0
+        budget = DUMP_LIMIT_BYTES - whole - header * len(names)
+        per = max(1, budget // max(1, len(rest) + (0 if whole else 1)) // 16)   # elements per sampled leaf (16 bytes: the widest element)
+        sample = {n: per for n in (rest if whole else names)}
+    os.makedirs(path, exist_ok=True)
+    g = torch.Generator().manual_seed(DUMP_SAMPLE_SEED)
+    written = 0
+    for n in names:
+        t = torch.stack([x.detach() for x in stacked[n]])
+        if sample and n in sample:
+            idx = torch.randint(0, t.numel(), (min(sample[n], t.numel()),), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        if t.is_complex():
+            t = torch.view_as_real(t)
+        a = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+        np.save(os.path.join(path, n + ".npy"), a)
+        written += a.nbytes
+    print(f"[bench] --dump-outputs: {len(names)} array(s), {written / 1e6:.1f} MB in {path}"
+          + (f" (all but the last a seeded sample of {next(iter(sample.values()))} elements)" if sample else ""), file=sys.stderr)
+
+
+def make_slices(C, H, W, indices, **kw):
+    """synthetic.make_slice for every index, on a few host threads (numpy's FFTs release the GIL).  Every slice draws from its own seed, so the
+    data do not depend on the number of threads."""
+    from concurrent.futures import ThreadPoolExecutor
+    from mridc_amd import synthetic
+    indices = list(indices)
+    n = max(1, min(16, len(indices), len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)))
+    with ThreadPoolExecutor(max_workers=n) as ex:
+        return list(ex.map(lambda i: synthetic.make_slice(C, H, W, slice_idx=i, **kw), indices))
+
+
 LAST_CONCURRENCY_CHECK = {}
 
 
@@ -373,7 +449,9 @@ def _replay_loop(step, datas, args):
                     outs[i] = step(datas[i])
     dist_barrier()
     elapsed, per_rank = rank_times(time.perf_counter() - t0, torch.device("cuda", torch.cuda.current_device()))
-    LAST_CONCURRENCY_CHECK["bit_identical"] = concurrent_replays_match_serial(graphs, streams, outs)
+    if args.dump_outputs and int(os.environ.get("RANK", "0")) == 0:
+        write_outputs(args.dump_outputs, outs)
+    LAST_CONCURRENCY_CHECK["bit_identical"] = concurrent_replays_match_serial(graphs, streams, outs) if args.full else None
     return elapsed, per_rank, bool(graphs), outs
 
 
@@ -465,7 +543,8 @@ def bench_qcirim(args, world, rank, dev, checks=False):
                config=dict(workload=f"qCIRIM 1 cascade x 8 time-steps, IndRNN 128 filters, 4 echoes, 32 coils, 256x256, {NS} slice(s) "
                                     f"per GPU and step ({NS} HIP stream(s), {'hipGraph' if graphed else 'eager'}), random-init weights" + (", trainer.precision = 16" if p16 else ""),
                            parallelism=f"slice-sharded x{world}"))
-    res["concurrent_replays_bit_identical_to_serial"] = conc_ok
+    if args.full:
+        res["concurrent_replays_bit_identical_to_serial"] = conc_ok
     if checks and rank == 0:
         direct = 2.0 * 128 * 128 * 9 * H * W
         msh, nh = timer.mean_ms("h3x3_128x128")
@@ -566,8 +645,7 @@ def bench_e2evn(args, world, rank, dev, checks=False):
     s0, s1 = shard_range(world * NS * B, rank, world)
     datas, hosts = [], []
     for i in range(NS):
-        slices = [synthetic.make_slice(C, H, W, slice_idx=j, mask_dtype=torch.float32 if args.model == "vsnet" else torch.uint8)
-                  for j in range(s0 + i * B, s0 + (i + 1) * B)]
+        slices = make_slices(C, H, W, range(s0 + i * B, s0 + (i + 1) * B), mask_dtype=torch.float32 if args.model == "vsnet" else torch.uint8)
         h_ = {k: torch.cat([s[k] for s in slices], 0) for k in ("y", "sensitivity_maps", "target")}
         h_["mask"] = slices[0]["mask"]
         hosts.append(h_)
@@ -600,7 +678,8 @@ def bench_e2evn(args, world, rank, dev, checks=False):
                config=dict(workload=f"{desc}, {C} coils, {H}x{W}, batch "
                                     f"{Bt} per GPU ({NS} concurrent HIP stream(s), {'one hipGraph each' if graphed else 'eager'}), random-init weights "
                                     "(seed 0)", parallelism=f"slice-sharded x{world}"))
-    res["concurrent_replays_bit_identical_to_serial"] = conc_ok
+    if args.full:
+        res["concurrent_replays_bit_identical_to_serial"] = conc_ok
     if checks and rank == 0:
         # dominant kernel: the U-Net's 3x3 convolutions (k_uconv: fp32 MFMA 16x16x4 blocks, InstanceNorm statistics from the accumulators,
         # normalisation + LeakyReLU of the PREVIOUS layer applied by the tile loader) -- the shape that takes the most time
@@ -748,6 +827,8 @@ def bench_train(args, world, rank, dev, checks=False):
         loss = step_fn(model, flat, opt, batch)
     dist_barrier()
     elapsed, per_rank = rank_times(time.perf_counter() - t0, dev)
+    if args.dump_outputs and rank == 0:            # what a caller of the step has afterwards: the step's loss and the updated parameters
+        write_outputs(args.dump_outputs, [dict(loss=torch.as_tensor(loss).reshape(1), parameters=flat.flat)])
     losses.append(float(loss))
     if args.model == "e2evn":
         return dict(metric=f"slices/sec (training), E2EVN {ucfg['num_cascades']}-cascade {C}-coil {H}x{W}", value=world * args.steps / elapsed,
@@ -1088,7 +1169,7 @@ def exact_route_line(args):
     error O(2^-24): the route the two-term fp16 default is judged against).  A child because the route is chosen once per process."""
     import subprocess
     env = dict(os.environ, MRIDC_AMD_ARITH="bf16x3")
-    cmd = [sys.executable, os.path.abspath(__file__), "--no-cpu-baseline", "--no-other-configs", "--no-stream-inputs", "--steps", "6", "--warmup", "2",
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--no-cpu-baseline", "--no-other-configs", "--no-stream-inputs", "--steps", "6", "--warmup", "2",
            "--coils", str(args.coils), "--height", str(args.height), "--width", str(args.width), "--mask", args.mask]
     try:
         out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
@@ -1107,10 +1188,10 @@ def training_line(args, model="cirim"):
     on what ran before it is not a measurement.  The child's whole record (roofline on the cell-backward kernel, parity against the three oracle
     arithmetics, CPU baseline) rides along."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--train", "--dtype", "bf16", "--steps", "4", "--warmup", "1", "--no-other-configs", "--no-stream-inputs",
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--train", "--dtype", "bf16", "--steps", "4", "--warmup", "1", "--no-other-configs", "--no-stream-inputs",
            "--coils", str(args.coils), "--height", str(args.height), "--width", str(args.width)] + (["--no-cpu-baseline"] if args.no_cpu_baseline else [])
     if model == "e2evn":        # E2EVN under the same trainer (SURVEY 8 row T): forward + loss + backward as one hipGraph replay
-        cmd = [sys.executable, os.path.abspath(__file__), "--train", "--model", "e2evn", "--steps", "6", "--warmup", "2", "--no-other-configs", "--no-stream-inputs",
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--train", "--model", "e2evn", "--steps", "6", "--warmup", "2", "--no-other-configs", "--no-stream-inputs",
                "--no-cpu-baseline", "--coils", str(args.coils), "--height", str(args.height), "--width", str(args.width)]
     try:
         out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
@@ -1127,7 +1208,7 @@ def rim5_line(args):
     """SURVEY 0.4's second figure: the eight cascades with FIVE time-steps each -- what RIMBlock(time_steps=5) runs when it is called directly
     (models/rim/rim_block.py:68,217); CIRIM rounds its config's 5 up to 8 (models/cirim.py:50-51: the headline).  A child process."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--no-cpu-baseline", "--no-other-configs", "--no-stream-inputs", "--steps", "8", "--warmup", "2",
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--no-cpu-baseline", "--no-other-configs", "--no-stream-inputs", "--steps", "8", "--warmup", "2",
            "--coils", str(args.coils), "--height", str(args.height), "--width", str(args.width), "--rim-steps", "5"]
     try:
         out = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
@@ -1143,7 +1224,7 @@ def mask2d_line(args):
     base_cirim_run.yaml:84-90): the data-consistency gradient is then the three-pass kernel chain.  A child process (a fresh model, no state shared
     with the 1-D run); its own roofline_fft record rides along."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--no-cpu-baseline", "--no-other-configs", "--no-stream-inputs", "--steps", "8", "--warmup", "2",
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--no-cpu-baseline", "--no-other-configs", "--no-stream-inputs", "--steps", "8", "--warmup", "2",
            "--coils", str(args.coils), "--height", str(args.height), "--width", str(args.width), "--mask", "2d"]
     try:
         out = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
@@ -1257,7 +1338,10 @@ def precision16_record(args, cfg, model, state_dict, timer, host, out, elapsed, 
                world_size_seen=world_seen(), per_rank_ms_per_step=[1e3 * t / args.steps for t in per_rank], launch="hipGraph replay" if graphed else "eager",
                roofline=roofline, breakdown_ms=dict(llg=msl, llg_gather_form=msg, conv_layer1=ms1, conv_layer2=ms2, rim_steps_per_slice=cfg["num_cascades"] * T_),
                concurrent_replays_bit_identical_to_serial=conc_ok)
-    if world == 1 and not args.no_cpu_baseline:
+    if not args.full:                           # a plain run recorded no per-kernel events: no roofline / breakdown records on its line
+        for k_ in ("roofline", "breakdown_ms", "concurrent_replays_bit_identical_to_serial"):
+            res.pop(k_)
+    if args.full and world == 1 and not args.no_cpu_baseline:
         n_cpu = args.cpu_cascades if 0 < args.cpu_cascades <= cfg["num_cascades"] else cfg["num_cascades"]
         try:
             host1 = {k: v[:1] if k != "mask" else v for k, v in host.items()}
@@ -1279,7 +1363,7 @@ def precision16_record(args, cfg, model, state_dict, timer, host, out, elapsed, 
 def precision16_line(args):
     """BASELINE's headline model in the reference's own inference precision (`trainer.precision: 16`): a child process of the default run."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--no-other-configs", "--no-stream-inputs", "--steps", "10", "--warmup", "3", "--precision", "16",
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--no-other-configs", "--no-stream-inputs", "--steps", "10", "--warmup", "3", "--precision", "16",
            "--coils", str(args.coils), "--height", str(args.height), "--width", str(args.width), "--cpu-slices", "1", "--cpu-cascades", "1"]     # (torch's CPU fp16 convolutions take ~7 s per RIM step on the GPU box's EPYC: one cascade of one slice, extrapolated)
     cmd += ["--no-cpu-baseline"] if args.no_cpu_baseline else []
     try:
@@ -1332,7 +1416,7 @@ def main():
     from mridc_amd.collections.reconstruction.models.cirim import CIRIM
 
     if args.train:
-        r_ = bench_train(args, world, rank, dev, checks=world == 1 and not args.no_cpu_baseline)
+        r_ = bench_train(args, world, rank, dev, checks=args.full and world == 1 and not args.no_cpu_baseline)
         if rank == 0:
             emit(r_)
         if use_dist:
@@ -1340,7 +1424,7 @@ def main():
         flush_result()
         return
     if args.model != "cirim":
-        r_ = (bench_qcirim if args.model == "qcirim" else bench_e2evn)(args, world, rank, dev, checks=world == 1 and not args.no_cpu_baseline)
+        r_ = (bench_qcirim if args.model == "qcirim" else bench_e2evn)(args, world, rank, dev, checks=args.full and world == 1 and not args.no_cpu_baseline)
         if rank == 0:
             emit(r_)
         if use_dist:
@@ -1365,8 +1449,10 @@ def main():
     from mridc_amd.sharding import shard_range
     s0, s1 = shard_range(world * NS * B, rank, world)
 
+    all_slices = make_slices(C, H, W, range(s0, s1))
+
     def make_host(first):
-        slices = [synthetic.make_slice(C, H, W, slice_idx=i) for i in range(first, first + B)]
+        slices = all_slices[first - s0:first - s0 + B]
         h_ = {k: torch.cat([s[k] for s in slices], 0) for k in ("y", "sensitivity_maps", "target")}
         h_["mask"] = slices[0]["mask"]
         if args.mask == "2d":                           # k-space re-masked with a 2-D pattern (keeps a fully sampled centre)
@@ -1380,8 +1466,9 @@ def main():
             h_["y"] = torch.cat([s["kspace"] for s in slices], 0) * m2
         return h_
 
-    hosts = [make_host(s0 + i * B) for i in range(NS)]
     assert s0 + NS * B == s1
+    hosts = [make_host(s0 + i * B) for i in range(NS)]
+    del all_slices
     host = hosts[0]
     datas = [{k: v.to(dev) for k, v in h_.items()} for h_ in hosts]
     data = datas[0]
@@ -1423,20 +1510,21 @@ def main():
     for _ in range(max(args.warmup, 1)):
         out = step()
     # Launch-bound inner loop (392 dependent kernels per step): capture the step once and replay it as a hipGraph.
-    # Per-kernel HIP events cannot be recorded inside a replay, so the kernel breakdown is measured on eager steps first.
-    timer.enabled = True
-    barrier()
-    try:
-        # the host needs ~10 us per eager launch, several kernels take less: park the GPU behind a spin kernel while the two timed steps
-        # are enqueued, so that every event pair brackets GPU execution and not the host's launch latency
-        torch.cuda._sleep(int(4e7))
-    except Exception:  # noqa: BLE001
-        pass
-    for _ in range(2):
-        step()
-    timer.calibrate()
-    barrier()
-    timer.enabled = False
+    # Per-kernel HIP events cannot be recorded inside a replay, so the kernel breakdown (--full) is measured on eager steps first.
+    if args.full:
+        timer.enabled = True
+        barrier()
+        try:
+            # the host needs ~10 us per eager launch, several kernels take less: park the GPU behind a spin kernel while the two timed steps
+            # are enqueued, so that every event pair brackets GPU execution and not the host's launch latency
+            torch.cuda._sleep(int(4e7))
+        except Exception:  # noqa: BLE001
+            pass
+        for _ in range(2):
+            step()
+        timer.calibrate()
+        barrier()
+        timer.enabled = False
     # One captured hipGraph per stream (392 dependent kernels per slice are launch-bound when issued eagerly).  Per-kernel HIP
     # events cannot be recorded inside a replay, so the kernel breakdown above was measured on eager steps.
     streams = bench_streams(NS)
@@ -1470,12 +1558,14 @@ def main():
                 if graphs:
                     graphs[i].replay()
                 else:
-                    o_ = step(datas[i])
+                    outs[i] = step(datas[i])
                     if i == 0:
-                        out = o_
+                        out = outs[i]
     barrier()
     elapsed, per_rank = rank_times(time.perf_counter() - t0, dev)
-    headline_conc_ok = concurrent_replays_match_serial(graphs, streams, outs)
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, outs)
+    headline_conc_ok = concurrent_replays_match_serial(graphs, streams, outs) if args.full else None
 
     if rank == 0 and args.precision == 16:
         emit(precision16_record(args, cfg, model, state_dict, timer, host, out, elapsed, per_rank, world, NS, B, graphed, headline_conc_ok))
@@ -1670,18 +1760,22 @@ def main():
                                      raw_ms=dict(llg=timer.raw_ms("llg372") or timer.raw_ms("llg"), conv_layer1=timer.raw_ms("conv_layer1"),
                                                  conv_layer2=timer.raw_ms("conv_layer2_f16t") or timer.raw_ms("conv_layer2_sbt") or timer.raw_ms("conv_layer2_sb") or timer.raw_ms("conv_layer2_wino") or timer.raw_ms("conv_layer2"),
                                                  final=timer.raw_ms("final_gather") or timer.raw_ms("final"))))
-        res["concurrent_replays_bit_identical_to_serial"] = headline_conc_ok
+        if args.full:
+            res["concurrent_replays_bit_identical_to_serial"] = headline_conc_ok
+        else:                                   # a plain run recorded no per-kernel events: no roofline / breakdown records on its line
+            for k_ in ("roofline", "roofline_fft", "breakdown_ms", "event_timing"):
+                res.pop(k_)
         res["config"]["arith"] = ("fp32 tensors and fp32 accumulation; the two RIM layers multiply two-term fp16 operands (x = (h1 + h2) 2^-k, 22 significant "
                                   "bits, block-scaled by powers of two; three of the four term products) on v_mfma_f32_32x32x16_f16: error against float64 "
                                   "equal to the fp32-MFMA kernels' (2e-7); FFT / data consistency in fp32 vector arithmetic")
-        if world == 1 and not args.no_other_configs:
+        if args.full and world == 1 and not args.no_other_configs:
             res["exact_fp32_route"] = exact_route_line(args)
-        if world == 1 and args.stream_inputs:
+        if args.full and world == 1 and args.stream_inputs:
             res["streamed_inputs"] = streamed_inputs_run(args, step, hosts, datas, dev, NS * B)
             if os.environ.get("MRX_BENCH_STREAM_PROBE"):     # which part of the streamed loop costs what (upload, staging copy, event wait)
                 for v in ("no_h2d", "no_d2d", "no_wait", "full"):
                     print("[stream probe]", v, round(streamed_inputs_run(args, step, hosts, datas, dev, NS * B, variant=v)["value"], 2), file=sys.stderr)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             n_cpu = args.cpu_cascades if 0 < args.cpu_cascades <= cfg["num_cascades"] else cfg["num_cascades"]
             try:
                 host1 = {k: v[:1] if k != "mask" else v for k, v in host.items()}
@@ -1693,7 +1787,7 @@ def main():
             except Exception as ex:  # noqa: BLE001
                 res["cpu_baseline"] = dict(value=None, unit="slices/s", cores=os.cpu_count(), kind="port",
                                            sample=f"failed: {type(ex).__name__}: {ex}")
-        if world == 1 and not args.no_other_configs:
+        if args.full and world == 1 and not args.no_other_configs:
             # BASELINE.json configs 1, 3, 4 next to the headline, each with its own roofline / cpu_baseline / parity records (short runs:
             # the driver times this whole process)
             del model, datas, data
@@ -1705,6 +1799,7 @@ def main():
                                    ("qcirim_4echo_32coil_256x256", bench_qcirim, dict(model="qcirim", batch=1, streams=6, steps=10, warmup=2)),     # (streams 4 / 6 / 8: 740 / 790 / 781 slices/s, tools/runs/r06x.sh)
                                    ("qcirim_precision16_4echo_32coil_256x256", bench_qcirim, dict(model="qcirim", batch=1, streams=6, steps=10, warmup=2, precision=16, cpu_slices=1))):
                 a2 = copy.copy(args)
+                a2.dump_outputs = None                  # (the headline's outputs only)
                 for k_, v_ in over.items():
                     setattr(a2, k_, v_)
                 try:

@@ -435,6 +435,45 @@ def test_bench_line_is_short():
     assert "print(json.dumps(compact_line(res)), flush=True)" in src and src.count("print(json.dumps(res)") == 0
 
 
+def test_bench_dump_outputs_is_bounded_and_reproducible(tmp_path):
+    """`bench.py --dump-outputs DIR`: the headline's nested output (two streams of list[cascade][time_step] complex images) as float32 .npy files
+    under the size limit -- the last leaf (the final image) whole, the others as a seeded sample that is the same from run to run."""
+    import importlib.util
+    import os
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_module_dump", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(3)
+
+    def outs():
+        return [[[torch.randn(2, 40, 30, dtype=torch.complex64, generator=g) for _ in range(3)] for _ in range(2)] for _ in range(2)]
+
+    small = outs()
+    bench.write_outputs(str(tmp_path / "a"), small)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(f"out_{c}_{t}.npy" for c in range(2) for t in range(3))
+    a = np.load(tmp_path / "a" / "out_1_2.npy")
+    assert a.dtype == np.float32 and a.shape == (2, 2, 40, 30, 2)
+    assert np.array_equal(a[1], torch.view_as_real(small[1][1][2]).numpy())
+    big = outs()
+    limit = bench.DUMP_LIMIT_BYTES
+    try:
+        bench.DUMP_LIMIT_BYTES = 100000                     # smaller than the set (6 leaves of 2 x 2 x 40 x 30 x 8 bytes), larger than twice its last leaf
+        bench.write_outputs(str(tmp_path / "b"), big)
+        bench.write_outputs(str(tmp_path / "c"), big)
+    finally:
+        bench.DUMP_LIMIT_BYTES = limit
+    total = sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b"))
+    assert total <= 100000
+    assert np.array_equal(np.load(tmp_path / "b" / "out_1_2.npy"), torch.view_as_real(torch.stack([o[1][2] for o in big])).numpy())
+    s = np.load(tmp_path / "b" / "out_0_0.npy")
+    assert s.ndim == 2 and s.shape[1] == 2 and 0 < s.shape[0] < 2 * 2 * 40 * 30
+    for f in os.listdir(tmp_path / "b"):
+        assert np.array_equal(np.load(tmp_path / "b" / f), np.load(tmp_path / "c" / f)), f
+
+
 def _fake_kfd(tmp_path, readable_gpus):
     """A KFD topology like the MI355X hosts': two CPU nodes (KFD 0, 1) with four GPUs each as PCIe links (KFD 2-5, 6-9); only `readable_gpus` may be opened."""
     base = tmp_path / "class/kfd/kfd/topology/nodes"
